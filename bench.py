@@ -8,8 +8,16 @@ uploaded once and resident in HBM before timing; the attachment CLEAR is fused
 into the tile pass.  `value` is whole-job throughput: triangles of all frames /
 max-over-ranks wall time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...      (N > 1, RCCL gather)
+
+A plain run does only what `value` needs: it sets up, runs W warm-up frames,
+times K frames, writes the last timed frame's attachments when --dump-outputs
+is given (dump_outputs) and prints the result line.  --full adds everything
+else the line can carry, each from a pass of its own after the timed one: the
+cold-cache pass over rotated input copies, the event-timed per-kernel pass,
+the winner census and the roofline objects built from them, the quoted
+rocprofv3 profiles and the CPU baseline.
 
 Without a launcher (WORLD_SIZE unset) and N > 1 (or --force-dist), this process
 touches no GPU: it starts N worker processes of itself (one per GPU, ranks and a
@@ -46,10 +54,18 @@ def parse():
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--config", default="c2", choices=sorted(scenes.CONFIGS))
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample length")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write the last timed frame's attachments as DIR/color.npy and "
+                        "(1 GPU) DIR/depth.npy, float32, at most 64 MB in all (dump_outputs)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also run the cold-cache pass, the per-kernel and census passes "
+                        "(kernels, roofline, quoted profiles) and the CPU baseline; the options below that "
+                        "shape those passes only matter with it")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline sample length")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--cold-copies", type=int, default=3, metavar="K",
-                   help="value_cold: a second timed pass cycling K uploaded copies of the geometry frame to "
+                   help="--full: "
+                        "value_cold: a second timed pass cycling K uploaded copies of the geometry frame to "
                         "frame (K=3 puts C2's 360 MB of input past the 256 MiB Infinity Cache: the HBM-honest "
                         "rate, SURVEY.md §8d); 0 skips it")
     p.add_argument("--emulate-shard", type=int, default=0, metavar="G",
@@ -198,6 +214,31 @@ def cpu_baseline(scene, seconds, max_frames=500):
             "kind": "port", "nproc": threads, "nproc_all": total, "cpu_model": model,
             "sample": f"{frames} full frames of {scene.name} ({scene.triangles} tris, {scene.width}x{scene.height}) "
                       f"after 1 warm-up; {dt:.2f} s wall on {threads} threads (nproc; {total} CPUs online, {model})"}
+
+
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs: all files together
+DUMP_SEED = 20240607             # the pixel sample of a frame past the budget
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each per-pixel array of ``arrays`` (name -> (H, W, ...), all
+    of one H x W) as ``path``/<name>.npy in float32 (exact for 8-bit texels and f32
+    depth).  A frame whose arrays pass DUMP_BUDGET_BYTES is written as the same
+    seeded sample of its pixels from every array, (pixels, channels) in ascending
+    pixel order: fixed by DUMP_SEED and the frame size, so two builds sample alike."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    first = next(iter(arrays.values()))
+    pixels = first.shape[0] * first.shape[1]
+    per_pixel = sum(4 * (a.size // pixels) for a in arrays.values())
+    keep = (DUMP_BUDGET_BYTES - 4096 * len(arrays)) // per_pixel  # (4096: room for each file's header)
+    idx = None
+    if pixels > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(pixels, size=keep, replace=False))
+    for name, a in arrays.items():
+        if idx is not None:
+            a = a.reshape(pixels, -1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 class CaptureExchange(shard.Exchange):
@@ -448,6 +489,8 @@ def main():
     if a.emulate_shard > 1:
         if distributed:
             raise SystemExit("--emulate-shard is a 1-GPU diagnostic")
+        if a.dump_outputs:
+            raise SystemExit("--emulate-shard renders one shard's rows at a time: no whole frame for --dump-outputs")
         print(json.dumps(emulate(a, scene, cuda)), file=json_out, flush=True)
         return
     dev = rhi.RenderDevice(local)
@@ -462,8 +505,8 @@ def main():
               for i, t in enumerate(color_ts)]
     color = colors[0]
     depth = rhi.Texture(dev, rhi.TextureDesc.new_depth("frame.depth", W, H), depth_t.data_ptr())
-    # copy 0 is the warm (value) pass's geometry; copies 0..K-1 cycle in the cold pass
-    rs = [renderer.SceneRenderer(dev, scene) for _ in range(max(1, a.cold_copies))]
+    # copy 0 is the warm (value) pass's geometry; copies 0..K-1 cycle in --full's cold pass
+    rs = [renderer.SceneRenderer(dev, scene) for _ in range(max(1, a.cold_copies if a.full else 1))]
     shard_g = world
     exchange = None
     runtime_comm = distributed and a.comm == "runtime"
@@ -569,6 +612,67 @@ def main():
     # the Infinity Cache from frame to frame, as in the reference's static scene
     elapsed, enq = timed_pass(1)
     host_submit, host_gather = host_t[0], host_t[1]
+    stats = dev.last_draw_stats()  # (refreshed at the pass's closing wait_idle)
+    if a.dump_outputs and rank == 0:
+        # the last timed frame's attachments, as the caller holds them after the
+        # closing sync: the colour target it drew (rank 0's holds every rank's rows
+        # once gathered) and, on one GPU, the depth
+        arrays = {"color": color_ts[(frame[0] - 1) % nbuf].cpu().numpy().reshape(H, W, 4)}
+        if world == 1:
+            arrays["depth"] = depth_t.cpu().numpy()
+        dump_outputs(a.dump_outputs, arrays)
+
+    ms_per_step = elapsed / a.steps * 1e3
+    value = N * a.steps / elapsed / 1e6
+    b_in = scenes.config_bytes_per_triangle(a.config)
+    frame_bytes = N * b_in + W * H * 8
+    out = {
+        "metric": METRIC, "value": round(value, 2), "unit": "Mtri/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic (SplitMix64 triangle soup, SURVEY.md §8d)",
+        "config": {"workload": (f"{a.config}: {N} tris (reference asset, mesh.slang camera), {W}x{H}, "
+                                f"D32 GREATER (reverse-Z), B8G8R8A8_SRGB" if scene.program == scenes.PROGRAM_MESH else
+                                f"{a.config}: {N} tris soup, {W}x{H}, "
+                                f"{'Blinn-Phong' if scene.program == scenes.PROGRAM_BLINN_PHONG else 'flat'} "
+                                f"+ D32 LESS, B8G8R8A8_SRGB"),
+                   "triangles": N, "width": W, "height": H, "tile": shard.TILE, "input_copies": 1,
+                   "parallelism": f"tile-rows x{world}" + (
+                       f", {a.setup} setup" + (" (RCCL all-to-all)" if exchange is not None else "")
+                       + f" + RCCL row gather ({'runtime' if runtime_comm else 'torch'} communicators)"
+                       if distributed else "")},
+        "fps": round(1e3 / ms_per_step, 2),
+        "host_enqueue_ms_per_step": round(enq / a.steps * 1e3, 4),
+        "host_submit_ms_per_step": round(host_submit / a.steps * 1e3, 4),
+        "host_gather_ms_per_step": round(host_gather / a.steps * 1e3, 4),
+        "frame_alg_bytes": frame_bytes,
+        "frame_gbps": round(frame_bytes / (ms_per_step * 1e-3) / 1e9, 1),
+        "build": buildinfo.source_hash(),
+        "bin_pairs": stats["bin_pairs"],
+        "triangles_setup": stats["triangles_setup"],
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), file=json_out, flush=True)
+        if stream_ctx is not None:
+            dev.wait_idle()
+            stream_ctx.__exit__(None, None, None)
+        for row in encs:
+            for e in row:
+                e.destroy()
+        for c in colors:
+            c.destroy()
+        depth.destroy()
+        dev.close()
+        if distributed:
+            dist.destroy_process_group()
+
+    if not a.full:
+        finish()
+        return
+
+    # ---- --full: every further figure, each from a pass of its own
     # cold pass: K copies cycled, so every frame's vertex reads come from HBM
     elapsed_cold = timed_pass(len(rs))[0] if len(rs) > 1 else None
 
@@ -607,7 +711,6 @@ def main():
     dev.kernel_times(reset=True)
     pairs = stats["bin_pairs"]
     pixels = shard.owned_pixels(W, H, rank, shard_g)
-    b_in = scenes.config_bytes_per_triangle(a.config)
     n_setup, n_route = N, 0
     index_size = 4 if scene.index_type == scenes.INDEX_U32 else (2 if scene.index_type == scenes.INDEX_U16 else 0)
     if exchange is not None:  # this rank's range and the triangles it received
@@ -644,36 +747,13 @@ def main():
     design_total = sum(design.values())
     achieved_design = round(design_total / (tile_us * 1e-6) / 1e9, 1) if tile_us > 0 else None
 
-    ms_per_step = elapsed / a.steps * 1e3
-    value = N * a.steps / elapsed / 1e6
-    frame_bytes = N * b_in + W * H * 8
-    out = {
-        "metric": METRIC, "value": round(value, 2), "unit": "Mtri/s", "n_gpus": world, "steps": a.steps,
-        "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic (SplitMix64 triangle soup, SURVEY.md §8d)",
+    out.update({
         **({"value_cold": round(N * a.steps / elapsed_cold / 1e6, 2),
             "ms_per_step_cold": round(elapsed_cold / a.steps * 1e3, 4),
             "cold_copies": len(rs)} if elapsed_cold else {}),
-        "config": {"workload": (f"{a.config}: {N} tris (reference asset, mesh.slang camera), {W}x{H}, "
-                                f"D32 GREATER (reverse-Z), B8G8R8A8_SRGB" if scene.program == scenes.PROGRAM_MESH else
-                                f"{a.config}: {N} tris soup, {W}x{H}, "
-                                f"{'Blinn-Phong' if scene.program == scenes.PROGRAM_BLINN_PHONG else 'flat'} "
-                                f"+ D32 LESS, B8G8R8A8_SRGB"),
-                   "triangles": N, "width": W, "height": H, "tile": shard.TILE, "input_copies": 1,
-                   "parallelism": f"tile-rows x{world}" + (
-                       f", {a.setup} setup" + (" (RCCL all-to-all)" if exchange is not None else "")
-                       + f" + RCCL row gather ({'runtime' if runtime_comm else 'torch'} communicators)"
-                       if distributed else "")},
-        "fps": round(1e3 / ms_per_step, 2),
         "ms_per_step_profiled": round((tp1 - tp0) / a.steps * 1e3, 4),
-        "host_enqueue_ms_per_step": round(enq / a.steps * 1e3, 4),
         "frame_ms_median_profiled": round(frame_ms[len(frame_ms) // 2], 4),
         "frame_ms_p90_profiled": round(frame_ms[min(len(frame_ms) - 1, (9 * len(frame_ms)) // 10)], 4),
-        "host_submit_ms_per_step": round(host_submit / a.steps * 1e3, 4),
-        "host_gather_ms_per_step": round(host_gather / a.steps * 1e3, 4),
-        "frame_alg_bytes": frame_bytes,
-        "frame_gbps": round(frame_bytes / (ms_per_step * 1e-3) / 1e9, 1),
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
                      "peak_source": "MI355X_MICROARCH.md measured float4 copy (SURVEY.md §8d)",
@@ -696,28 +776,12 @@ def main():
         # the same kernels' rocprofv3 kernel-trace averages for this build (no events
         # between launches), beside the event-timed `kernels` above
         "kernels_rocprof": kernels_rocprof, "kernels_rocprof_source": kt_src,
-        "build": buildinfo.source_hash(),
-        "bin_pairs": pairs,
-        "triangles_setup": stats["triangles_setup"],
-    }
+    })
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(scene, a.cpu_seconds)
     elif rank == 0:
         out["cpu_baseline"] = None
-    if rank == 0:
-        print(json.dumps(out), file=json_out, flush=True)
-    if stream_ctx is not None:
-        dev.wait_idle()
-        stream_ctx.__exit__(None, None, None)
-    for row in encs:
-        for e in row:
-            e.destroy()
-    for c in colors:
-        c.destroy()
-    depth.destroy()
-    dev.close()
-    if distributed:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -80,15 +80,27 @@ def render_bytes(scene):
     return blobs
 
 
+def unpack_cerberus(dest):
+    """The reference's content/mesh/cerberus asset as the loader reads it, from the
+    copy kept under tests/golden/cerberus/ (scene.gltf as is, its buffer scene.bin
+    gzip'd; the textures it names are not kept: the mesh bake reads none).
+    Returns the path of ``dest``/scene.gltf."""
+    import shutil
+    os.makedirs(dest, exist_ok=True)
+    shutil.copy(os.path.join(HERE, "cerberus", "scene.gltf"), os.path.join(dest, "scene.gltf"))
+    with gzip.open(os.path.join(HERE, "cerberus", "scene.bin.gz"), "rb") as src, \
+            open(os.path.join(dest, "scene.bin"), "wb") as dst:
+        shutil.copyfileobj(src, dst)
+    return os.path.join(dest, "scene.gltf")
+
+
 def bake_cerberus():
-    """tests/golden/cerberus.mesh.npz: /root/reference/content/mesh/cerberus/scene.gltf
-    baked as zenith-asset's gltf_loader does (zenith_amd.assets).  Only where the
-    reference is mounted; the GPU box and later rounds use the committed file."""
+    """tests/golden/cerberus.mesh.npz: the cerberus asset (unpack_cerberus) baked
+    as zenith-asset's gltf_loader does (zenith_amd.assets)."""
+    import tempfile
     from zenith_amd import assets
-    src = "/root/reference/content/mesh/cerberus/scene.gltf"
-    if not os.path.exists(src):
-        return
-    v, i = assets.load_gltf_meshes(src)[0]
+    with tempfile.TemporaryDirectory() as tmp:
+        v, i = assets.load_gltf_meshes(unpack_cerberus(tmp))[0]
     np.savez_compressed(os.path.join(HERE, "cerberus.mesh.npz"), vertices=v, indices=i)
 
 

@@ -1,6 +1,7 @@
 """bench.py's contract: the per-pass algorithmic bytes of SURVEY.md §8d and, on
-the GPU, the one JSON line the driver parses (keys, roofline and CPU-baseline
-objects, the cold-cache pass over rotated input copies)."""
+the GPU, the one JSON line the driver parses: a plain run's headline keys and
+its --dump-outputs files, and with --full the roofline and CPU-baseline objects
+and the cold-cache pass over rotated input copies."""
 import json
 import os
 import subprocess
@@ -76,10 +77,10 @@ def test_quoted_profiles_name_this_build():
 
 @pytest.mark.gpu
 def test_bench_json_line():
-    """One short C1 run with a two-copy cold pass, as a child process: stdout holds
+    """One short C1 --full run with a two-copy cold pass, as a child process: stdout holds
     exactly one JSON line with the contract's keys (SURVEY.md §8d extras included)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "4", "--warmup", "2",
-           "--cold-copies", "2", "--cpu-seconds", "0.5"]
+           "--full", "--cold-copies", "2", "--cpu-seconds", "0.5"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -103,6 +104,75 @@ def test_bench_json_line():
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0
     assert cb["nproc"] == cb["cores"] and cb["nproc_all"] >= cb["nproc"] and cb["cpu_model"]
     assert set(d["kernels"]) >= {"setup_bin", "tile"}
+
+
+PLAIN_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config")
+FULL_ONLY_KEYS = ("roofline", "kernels", "kernels_rocprof", "cpu_baseline", "value_cold", "ms_per_step_profiled")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_frame(tmp_path):
+    """A plain run (no --full) times its steps and nothing else: the line keeps
+    the headline keys and carries none of --full's objects, and --dump-outputs
+    leaves the last timed frame's colour and depth as float32 .npy files, equal
+    to the oracle's frame of the same seeded scene (so a second run, or another
+    build, writes the same arrays)."""
+    import numpy as np
+    from oracle import oracle
+    from zenith_amd import scenes
+    dump = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c1", "--steps", "3",
+           "--warmup", "2", "--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=110)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    for k in PLAIN_KEYS:
+        assert k in d, k
+    for k in FULL_ONLY_KEYS:
+        assert k not in d, k
+    assert d["unit"] == "Mtri/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] > 0
+    # value is triangles / second of the timed steps; both figures are rounded
+    # (ms_per_step to 4 places, value to 2): twice the sum of the two half-ulps
+    slack = 2 * (d["value"] * 0.5e-4 / d["ms_per_step"] + 0.5e-2)
+    assert abs(d["value"] - 100_000 / (d["ms_per_step"] * 1e-3) / 1e6) <= slack
+    assert sorted(os.listdir(dump)) == ["color.npy", "depth.npy"]
+    assert sum(os.path.getsize(dump / f) for f in os.listdir(dump)) <= 64_000_000
+    color, depth = np.load(dump / "color.npy"), np.load(dump / "depth.npy")
+    assert color.dtype == np.float32 and depth.dtype == np.float32
+    oc, od = oracle.render(scenes.config_scene("c1"))
+    assert color.shape == oc.shape and np.array_equal(color, oc.astype(np.float32))
+    assert np.array_equal(depth.view(np.uint32), od.view(np.uint32))
+
+
+def test_dump_outputs_samples_a_frame_past_the_budget(tmp_path, monkeypatch):
+    """dump_outputs: arrays within the budget are written whole; past it, every
+    array holds the same seeded sample of pixels (the same one on every call), in
+    ascending pixel order, and the files together stay within the budget."""
+    import numpy as np
+    import bench
+    H, W = 48, 64
+    pix = np.arange(H * W, dtype=np.uint32)
+    color = np.stack([pix % 251, pix % 241, pix % 239, pix % 233], axis=1).astype(np.uint8).reshape(H, W, 4)
+    depth = pix.astype(np.float32).reshape(H, W)
+    bench.dump_outputs(str(tmp_path / "whole"), {"color": color, "depth": depth})
+    c = np.load(tmp_path / "whole" / "color.npy")
+    assert c.dtype == np.float32 and c.shape == (H, W, 4) and np.array_equal(c, color)
+    assert np.array_equal(np.load(tmp_path / "whole" / "depth.npy"), depth)
+    budget = 2 * 4096 + 20 * 1000  # room for exactly 1000 of the 3072 pixels
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", budget)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), {"color": color, "depth": depth})
+    ca, da = np.load(tmp_path / "a" / "color.npy"), np.load(tmp_path / "a" / "depth.npy")
+    assert ca.dtype == da.dtype == np.float32 and ca.shape == (1000, 4) and da.shape == (1000, 1)
+    idx = da[:, 0].astype(np.int64)  # depth holds each pixel's own index
+    assert np.all(np.diff(idx) > 0) and np.array_equal(ca, color.reshape(-1, 4)[idx])
+    assert np.array_equal(ca, np.load(tmp_path / "b" / "color.npy"))
+    assert np.array_equal(da, np.load(tmp_path / "b" / "depth.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= budget
 
 
 @pytest.mark.gpu

@@ -14,7 +14,7 @@ for r in $(seq $R); do
       lib=zenith_amd/variants/${v%%:*}/libzenith_raster.so
       [ "${v%%:*}" = prod ] && lib=zenith_amd/lib/libzenith_raster.so  # the in-tree build
       envs=""; [ "$v" != "${v#*:}" ] && envs=$(echo "${v#*:}" | tr ',' ' ')
-      env $envs ZR_LIB_PATH=$lib timeout -k 10 150 python bench.py --config $c --no-cpu-baseline --cold-copies 0 "$@" \
+      env $envs ZR_LIB_PATH=$lib timeout -k 10 150 python bench.py --config $c --full --no-cpu-baseline --cold-copies 0 "$@" \
         > "$O/$(echo $v | tr ":=," "---")_${c}_$r.json" 2>> $O/err.log || { echo "FAIL $v $c $r"; exit 1; }
       echo "$v $c $r done"
     done

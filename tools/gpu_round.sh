@@ -13,8 +13,8 @@ O=gpurun_out/$V
 mkdir -p $O
 if [ "$2" != pmc ]; then  # "pmc": the profiler passes only
 timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/pytest.log 2>&1 || exit 1
-timeout -k 10 300 python bench.py > $O/bench_c2.json 2> $O/bench.err || exit 2
-for c in c1 c3 c4 cerberus c2x c3x; do timeout -k 10 200 python bench.py --config $c --no-cpu-baseline > $O/bench_$c.json 2>> $O/bench.err || exit 3; done
+timeout -k 10 300 python bench.py --full > $O/bench_c2.json 2> $O/bench.err || exit 2
+for c in c1 c3 c4 cerberus c2x c3x; do timeout -k 10 200 python bench.py --config $c --full --no-cpu-baseline > $O/bench_$c.json 2>> $O/bench.err || exit 3; done
 for g in 2 4 8; do timeout -k 10 200 python bench.py --emulate-shard $g --no-cpu-baseline > $O/bench_c2_shard$g.json 2>> $O/bench.err || exit 3; done
 for c in c2 c3; do timeout -k 10 200 python bench.py --config $c --emulate-shard 8 --setup partitioned --no-cpu-baseline > $O/bench_${c}_shard8_part.json 2>> $O/bench.err || exit 3; done
 timeout -k 10 200 python bench.py --config c3 --emulate-shard 8 --no-cpu-baseline > $O/bench_c3_shard8.json 2>> $O/bench.err || exit 3
