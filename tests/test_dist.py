@@ -166,13 +166,13 @@ def test_route_blocks_overflow():
 
 def test_route_model_matches_device_constants():
     """The host route model uses the kernels' chunk size, entry and header sizes
-    (zr_internal.h) and the runtime's default capacity (zr_runtime.cpp)."""
+    (zr_internal.h) and the plan's default capacity (zr_plan.cpp)."""
     import re
     from zenith_amd import shard
     src = open(os.path.join(ROOT, "zenith_amd", "csrc", "zr_internal.h")).read()
     assert int(re.search(r"#define ZR_ROUTE_CHUNK (\d+)", src).group(1)) == shard.ROUTE_CHUNK
     assert 'sizeof(RouteEntry) == 48' in src and 'sizeof(RouteHeader) == 16' in src
-    rt = open(os.path.join(ROOT, "zenith_amd", "csrc", "zr_runtime.cpp")).read()
+    rt = open(os.path.join(ROOT, "zenith_amd", "csrc", "zr_plan.cpp")).read()
     assert "std::min<uint64_t>(span, (2 * span + G - 1) / G + 4096)" in rt and "if (G <= 2) return span;" in rt
     # 1M primitives over 8 ranks: span rounds ceil(N / G) up to whole chunks
     chunks, span, cap, bb = shard.route_geometry(1_000_000, 8)

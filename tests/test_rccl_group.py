@@ -1,6 +1,6 @@
 """The runtime's grouped point-to-point calls (zr_rccl.cpp rccl_grouped), which
 both collectives use -- the partitioned-setup exchange and the tile-row gather
-(zr_runtime.cpp rccl_exchange, zr_device_gather_tile_rows) -- against a fake
+(zr_multi.cpp rccl_exchange, zr_device_gather_tile_rows) -- against a fake
 RCCL loaded through ZR_RCCL_LIB (CPU only; no device is touched).
 
 A group is closed exactly when it was opened: a failed ncclGroupStart issues no

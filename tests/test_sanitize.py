@@ -5,10 +5,12 @@ CPU only (no GPU code is sanitized: the device side stays as built):
   scenes that cover every program, indexed / non-indexed / u16 draws,
   instancing, out-of-range indices, clipping and tile-row shards; each frame
   must equal the unsanitized oracle's;
-- the runtime's host code (zenith_amd/csrc/zr_runtime.cpp, zr_rccl.cpp) built
+- the runtime's host code (zenith_amd/csrc/*.cpp) built
   with hipcc -Xarch_host -fsanitize=..., exercised through the device-free paths
   of the C ABI (tests/sanitize/abi_host.c) and by examples/triangle.c, which on
-  a machine without a GPU must fail cleanly at zr_device_create.
+  a machine without a GPU must fail cleanly at zr_device_create;
+- the draw plan and the shape table (zenith_amd/csrc/zr_plan.cpp) alone, with the
+  stand-alone tests/sanitize/plan_host.cpp: no kernels, no device.
 Every build uses -fno-sanitize-recover=all, so any report ends the run non-zero.
 """
 import ctypes as C
@@ -114,16 +116,30 @@ def runtime_san(tmp_path_factory):
     host_san = [x for f in ("-fsanitize=address", "-fsanitize=undefined", "-fno-sanitize-recover=all",
                             "-fno-omit-frame-pointer") for x in ("-Xarch_host", f)]
     objs = []
-    for src in ("zr_runtime.cpp", "zr_rccl.cpp"):
-        o = str(d / (src + ".o"))
-        subprocess.run(hip + host_san + ["-x", "hip", "-c", os.path.join(ROOT, "zenith_amd", "csrc", src), "-o", o],
-                       check=True)
+    for src in sorted(glob.glob(os.path.join(ROOT, "zenith_amd", "csrc", "*.cpp"))):
+        o = str(d / (os.path.basename(src) + ".o"))
+        subprocess.run(hip + host_san + ["-x", "hip", "-c", src, "-o", o], check=True)
         objs.append(o)
     lib = str(d / "libzenith_raster_san.so")
     subprocess.run(["/opt/rocm/bin/hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", "-Xarch_host",
                     "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined", "-shared-libasan", "-o", lib,
                     *objs, kernels, "-ldl", "-Wl,-rpath,/opt/rocm/lib"], check=True)
     return str(d)
+
+
+def test_plan_host_sanitized(tmp_path):
+    """zr_plan.cpp (plan_draw, ShapeBook, read_knobs) against hand-derived values,
+    host code under ASan + UBSan, linked with nothing else of the library."""
+    exe = str(tmp_path / "plan_host")
+    csrc = os.path.join(ROOT, "zenith_amd", "csrc")
+    host_san = [x for f in ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer")
+                for x in ("-Xarch_host", f)]
+    subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"),
+                    "-I", csrc, "--offload-arch=gfx950", *host_san, "-x", "hip",
+                    os.path.join(ROOT, "tests", "sanitize", "plan_host.cpp"), os.path.join(csrc, "zr_plan.cpp"),
+                    "-fsanitize=address,undefined", "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=ENV)
+    assert r.returncode == 0 and "plan_host ok" in r.stdout, (r.stdout + r.stderr)[-4000:]
 
 
 def _build_c(runtime_san, src, exe):

@@ -1,6 +1,7 @@
 // zr_internal.h — data layout shared by the host runtime and the HIP kernels.
 // DESIGN.md §4 describes each buffer's HBM layout and the per-unit byte counts.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -393,6 +394,8 @@ struct DrawParams {
     // the parameters are grouped scalar loads)
     float push[kMaxPushWords];
 };
+// the kernel-argument layout (k_tile's grouped scalar reloads depend on it)
+static_assert(sizeof(DrawParams) == 728 && offsetof(DrawParams, push) == 596 && offsetof(DrawParams, tile_shift) == 592);
 
 // k_tile workgroup size for a pass of `ntiles` tiles on `cus` CUs: 4 waves per
 // tile while the pass has >= 6 tiles per CU, else 8 (tile-row shards: a tile's
@@ -403,6 +406,12 @@ struct DrawParams {
 // + the tile schedule's per-XCD bucket counts (8 x 64, the last workgroup only).
 constexpr uint32_t kSchedBuckets = 64;
 constexpr uint32_t kSetupMiscWords = 96 + 8 * kSchedBuckets;
+// k_setup_bin's dynamic LDS (the launcher's size; the host plan fits bboxes and staging beside the histograms)
+inline size_t setup_bin_lds_bytes(uint32_t ntiles, uint32_t bbox_entries, uint32_t stage_pairs = 0) {
+    const size_t nt4 = ((size_t)ntiles + 3u) / 4u * 4u;
+    return (nt4 + kSetupMiscWords) * sizeof(uint32_t) + (size_t)bbox_entries * sizeof(BBox) +
+           (stage_pairs ? nt4 * sizeof(uint32_t) + (size_t)stage_pairs * 8u : 0u);
+}
 // A draw of fewer than 32 primitives per tile (cerberus at 1080p: 16) also gets 8
 // waves: its few heavy tiles (large triangles) end the pass alone on their CUs
 // (cerberus tile pass 124 -> 113 us; C1, 49 per tile, is 14% slower at 8 waves).
@@ -473,7 +482,7 @@ inline uint32_t bin_slab_whole(uint32_t target, uint32_t max_tile) {
 
 // The bin buffer (entries) of a scratch set's first draw, before any draw has
 // been measured: twice the primitives plus 256 per tile.  That draw takes slabs of
-// a third of it (zr_runtime ensure_scratch) and the pool the rest, which holds
+// a third of it (zr_plan ShapeBook::sizes) and the pool the rest, which holds
 // the Gaussian-clustered c2x / c3x scenes' first frames without a dropped run.
 constexpr uint32_t kBinShrinkSyncs = 16;  // the runtime's bin-buffer shrink check interval (sync points)
 constexpr uint64_t kBinShrinkMin = 1ull << 24;  // ... and the least it frees (entries: 64 MiB)
@@ -489,7 +498,7 @@ inline uint64_t bin_default_capacity(uint64_t prims, uint32_t ntiles) {
 constexpr uint32_t kTileJobEntries = 2048;
 inline bool use_tile_jobs(uint32_t max_tile) { return max_tile > 4u * kTileJobEntries; }
 // Key buffers a draw shape not measured yet may get for its tile jobs (64 MiB;
-// zr_runtime ensure_scratch): afterwards a shape gets what its split needed.
+// zr_plan ShapeBook::sizes): afterwards a shape gets what its split needed.
 constexpr uint64_t kJobKeyBytesFirst = 64ull << 20;
 
 inline uint32_t records_setup_wgs(uint64_t entries, uint32_t cus) {
@@ -524,7 +533,7 @@ inline bool use_tile_schedule(uint32_t ntiles, uint32_t cus, uint32_t tile_threa
     return ntiles > slots && 32ull * prims < ((uint64_t)ntiles << (2u * tile_shift));  // (< 1/32 primitive per pixel)
 }
 
-// Draw i+1's setup beside draw i's tile pass (zr_device_t::setup_overlap): small
+// Draw i+1's setup beside draw i's tile pass (Knobs::setup_overlap): small
 // draws, tile-row shards, and draws of fewer primitives than pixels -- not a
 // draw whose HBM-bound setup is the frame (C4's 4.8 per pixel: +28 % beside its
 // tile pass; C2 -11 %, C3 -5 %, docs/EXPERIMENTS.md round 6).
@@ -585,7 +594,6 @@ __host__ __device__ inline ShardGeom shard_geom(const DrawParams& P) {
 
 // Launchers (zr_kernels.hip).  All enqueue on `stream`; no host synchronisation.
 void launch_setup_bin(const DrawParams& p, void* stream);  // setup + bin, one launch
-size_t setup_bin_lds_bytes(uint32_t ntiles, uint32_t bbox_entries, uint32_t stage_pairs = 0);
 const void* setup_bin_kernel(uint32_t batch, bool mesh);
 void launch_tile(const DrawParams& p, void* stream);
 void launch_clear(const DrawParams& p, void* stream);

@@ -2942,12 +2942,6 @@ __global__ __launch_bounds__(kTileThreads) void k_clear(DrawParams P) {
 
 static inline uint32_t blocks_for(uint32_t n, uint32_t per) { return (n + per - 1) / per; }
 
-size_t setup_bin_lds_bytes(uint32_t ntiles, uint32_t bbox_entries, uint32_t stage_pairs) {
-    const size_t nt4 = ((size_t)ntiles + 3u) / 4u * 4u;
-    return (nt4 + kSetupMiscWords) * sizeof(uint32_t) + (size_t)bbox_entries * sizeof(BBox) +
-           (stage_pairs ? nt4 * sizeof(uint32_t) + (size_t)stage_pairs * 8u : 0u);
-}
-
 const void* setup_bin_kernel(uint32_t batch, bool mesh) {
     if (mesh) return reinterpret_cast<const void*>(&k_setup_bin<1, true>);
     switch (batch) {

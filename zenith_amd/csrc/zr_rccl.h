@@ -30,7 +30,7 @@ bool rccl_recv(void* buf, size_t bytes, int peer, void* comm, hipStream_t s, std
 // ncclGroupEnd -- only when the start succeeded, and always then, whatever the
 // sends returned (an unbalanced start or end is an RCCL error of its own and
 // would hide the first one's message).  Both collectives go through it
-// (zr_runtime.cpp); tests/test_rccl_group.py drives it against a fake RCCL.
+// (zr_multi.cpp); tests/test_rccl_group.py drives it against a fake RCCL.
 struct P2POp {
     void* buf;
     size_t bytes;

@@ -85,7 +85,7 @@ class TileGather:
 # rank sets up 1/G of a draw's primitives and ships each set-up primitive to the
 # ranks owning the tile rows it touches; the blocks travel in one all-to-all per
 # draw.  Host model of the device layout (zr_internal.h RouteEntry / RouteHeader,
-# zr_runtime.cpp exec_draw): rank r routes primitives [r * span, (r + 1) * span)
+# zr_plan.cpp plan_draw): rank r routes primitives [r * span, (r + 1) * span)
 # with span = ceil(ceil(N / G) / ROUTE_CHUNK) * ROUTE_CHUNK; its block for one
 # destination is a 16-B header (u32 pad, u32 total, 2 pad) then `cap` 48-B
 # entries (32-B compact record, u32 bb0, u32 bb1, u32 draw id, pad).  The device
@@ -102,7 +102,7 @@ assert _ENTRY.itemsize == ENTRY_BYTES and _HEADER.itemsize == HEADER_BYTES
 
 
 def capacity_default(span: int, world: int) -> int:
-    """zr_runtime.cpp route_capacity_default: entries per block when the caller sets none."""
+    """zr_plan.cpp route_capacity_default: entries per block when the caller sets none."""
     return span if world <= 2 else min(span, -(-2 * span // world) + 4096)
 
 
