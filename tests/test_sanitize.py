@@ -10,7 +10,9 @@ CPU only (no GPU code is sanitized: the device side stays as built):
   of the C ABI (tests/sanitize/abi_host.c) and by examples/triangle.c, which on
   a machine without a GPU must fail cleanly at zr_device_create;
 - the draw plan and the shape table (zenith_amd/csrc/zr_plan.cpp) alone, with the
-  stand-alone tests/sanitize/plan_host.cpp: no kernels, no device.
+  stand-alone tests/sanitize/plan_host.cpp: no kernels, no device;
+- the kernels' host + device index arithmetic (zenith_amd/csrc/zr_order.h) alone, with
+  the stand-alone tests/sanitize/order_host.cpp.
 Every build uses -fno-sanitize-recover=all, so any report ends the run non-zero.
 """
 import ctypes as C
@@ -140,6 +142,22 @@ def test_plan_host_sanitized(tmp_path):
                     "-fsanitize=address,undefined", "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=ENV)
     assert r.returncode == 0 and "plan_host ok" in r.stdout, (r.stdout + r.stderr)[-4000:]
+
+
+def test_order_host_sanitized(tmp_path):
+    """zr_order.h (XCD tile order, tile jobs, tile_order items, cost class, lane space of
+    a sorted segment) against hand-derived values: the header alone, host code under
+    ASan + UBSan, its own process."""
+    exe = str(tmp_path / "order_host")
+    csrc = os.path.join(ROOT, "zenith_amd", "csrc")
+    host_san = [x for f in ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer")
+                for x in ("-Xarch_host", f)]
+    subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"),
+                    "-I", csrc, "--offload-arch=gfx950", *host_san, "-x", "hip",
+                    os.path.join(ROOT, "tests", "sanitize", "order_host.cpp"),
+                    "-fsanitize=address,undefined", "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=ENV)
+    assert r.returncode == 0 and "order_host ok" in r.stdout, (r.stdout + r.stderr)[-4000:]
 
 
 def _build_c(runtime_san, src, exe):

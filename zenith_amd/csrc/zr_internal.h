@@ -507,7 +507,7 @@ inline uint32_t records_setup_wgs(uint64_t entries, uint32_t cus) {
 }
 
 // Whether k_tile's 512-thread resolve reads its winners' records from the tile's
-// LDS record table (zr_kernels.hip rec_table_insert): for draws of >= 256
+// LDS record table (zr_resolve.h rec_table_insert): for draws of >= 256
 // primitives per screen tile.  There most winners are distinct small primitives
 // and the table saves one gather each (C2, 490 per tile: tile pass 72.4 -> 65.8
 // us); with fewer, larger primitives per tile their pixels' record requests
